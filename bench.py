@@ -16,10 +16,22 @@ gather step after it -- --exchange ipc, the default).  --exchange gather keeps t
 IPC mapping fails.  Per-step work is fixed as N grows ("scaling": "strong"), so N = 1 is exactly the
 BENCH workload.  --partition frames instead gives each rank its own turntable views (no collective).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--views V] [--no-cpu-baseline]
-                    [--exchange ipc|gather] [--cpu-pixels P] [--dump-images PATH]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--views V] [--dump-outputs DIR] [--full]
+                    [--exchange ipc|gather] [--no-cpu-baseline] [--cpu-pixels P] [--dump-images PATH]
 
 Prints ONE JSON line on rank 0.  `value` = rays (intersect() calls) of the step / max-rank time.
+
+A plain run does only what that figure needs: scene set-up, W warm-up steps, the K timed steps, the result line.
+--full adds everything else the line can carry, each from runs of its own: the counting pass behind `roofline`,
+`config.ray_mix` and `config.ub_regime_hits`, the rocprofv3 --pmc passes behind `roofline.traffic` / `issue` /
+`cache_ceiling`, the single-frame latency record, the warm scene upload time and the CPU baseline legs
+(--no-pmc, --no-single-frame and --no-cpu-baseline leave single parts of it out).
+
+--dump-outputs DIR writes what the last timed step computed, before anything else renders: DIR/images.npy
+(float32 [n][3]: the step's pixels, F x H x W of them in image order; a step of more than DUMP_PIXELS pixels is
+sampled at the sorted indices np.random.default_rng(DUMP_SEED).integers(0, F * H * W, DUMP_PIXELS)) and
+DIR/rays.npy (float64 [1]: the step's ray count, as its rt_stats reports it).  Scene, cameras and options are
+fixed by the arguments, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import hashlib
@@ -57,6 +69,28 @@ DEFAULT_VIEWS = 64  # frames per step: a 64-view turntable (5.625 deg apart) of 
 # take ~10 ms per frame; a C5 4K frame (3 x 64 plane-light samples, glass to depth 8: ~1e9 rays) fills the GPU
 # on its own, and batching its views measured slower per ray (2 900 vs 2 556 Mrays/s for 8 views, r02)
 CONFIG_VIEWS = {"C1": 64, "C2": 64, "C3": DEFAULT_VIEWS, "C4": 16, "C5": 1}
+# --dump-outputs: at most this many pixels of the step (3 float32 each: 48 MB), a fixed sample of a larger step
+DUMP_PIXELS = 4_000_000
+DUMP_SEED = 20240613
+
+
+def dump_outputs(path, pixels, rays):
+    """--dump-outputs (rank 0): the last timed step's images and ray count as .npy files under path.
+    pixels: the step's images as [F * H * W][3] float32, a torch device tensor or a host array."""
+    os.makedirs(path, exist_ok=True)
+    n = int(pixels.shape[0])
+    if n > DUMP_PIXELS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_PIXELS))
+        if isinstance(pixels, np.ndarray):
+            pixels = pixels[idx]
+        else:  # gathered on the device: only the sample crosses to the host
+            import torch
+
+            pixels = pixels[torch.from_numpy(idx).to(pixels.device)]
+    if not isinstance(pixels, np.ndarray):
+        pixels = pixels.cpu().numpy()
+    np.save(os.path.join(path, "images.npy"), np.ascontiguousarray(pixels, dtype=np.float32))
+    np.save(os.path.join(path, "rays.npy"), np.array([float(rays)], dtype=np.float64))
 
 
 def algorithmic_bytes(st, pixels):
@@ -245,6 +279,11 @@ def main():
     ap.add_argument("--dump-images", default=None, help="rank 0 saves the last step's images (.npy; tests)")
     ap.add_argument("--no-pmc", action="store_true",
                     help="skip the two rocprofv3 --pmc passes that measure roofline.traffic (N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the counting pass (roofline, ray mix), the rocprofv3 --pmc passes, the "
+                         "single-frame latency record, the warm scene upload time and the CPU baseline legs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's outputs to DIR/images.npy and DIR/rays.npy")
     args = ap.parse_args()
     if args.views is None:
         args.views = CONFIG_VIEWS.get(args.config, DEFAULT_VIEWS)
@@ -288,10 +327,12 @@ def main():
     t_up = time.perf_counter()
     ctx = R.Context(scene, device=local)
     upload_cold_s = time.perf_counter() - t_up
-    ctx.close()
-    t_up = time.perf_counter()
-    ctx = R.Context(scene, device=local)
-    upload_s = time.perf_counter() - t_up
+    upload_s = None
+    if args.full:
+        ctx.close()
+        t_up = time.perf_counter()
+        ctx = R.Context(scene, device=local)
+        upload_s = time.perf_counter() - t_up
     build_info = ctx.build_info()
 
     img_elems = F * W * H * 3
@@ -367,12 +408,14 @@ def main():
         return st
 
     # counting pass (same kernel, COUNT=true) for the algorithmic-byte roofline numerator and the
-    # count of hits in the reference's undefined-barycentrics regime
-    R.set_counting(True)
-    cst = step()
-    R.set_counting(False)
-    # lane use of the traversal (counting build): lane node visits / (64 x wave node steps), same for records
-    cdbg = [int(x) for x in ctx.debug_counters()[:28]]
+    # count of hits in the reference's undefined-barycentrics regime (--full: a launch of its own)
+    cst, cdbg = None, None
+    if args.full:
+        R.set_counting(True)
+        cst = step()
+        R.set_counting(False)
+        # lane use of the traversal (counting build): lane node visits / (64 x wave node steps), same for records
+        cdbg = [int(x) for x in ctx.debug_counters()[:28]]
     for _ in range(args.warmup):
         step()
 
@@ -393,9 +436,15 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
 
+    if args.dump_outputs and rank == 0 and st is not None:
+        # the last timed step's images, before anything below renders into them (N > 1: rank 0 holds every rank's
+        # pixels unless --exchange none; rays is rank 0's launch)
+        px = R.device_to_host(img_ptr, img_elems) if exchange == "ipc" else images
+        dump_outputs(args.dump_outputs, px.reshape(-1, 3), st.rays)
+
     # single-frame latency beside the batch: the default view alone (this rank's bands), one launch
     single = None
-    if F > 1 and not args.no_single_frame:
+    if args.full and F > 1 and not args.no_single_frame:
         one_cam = [R.camera_from_trackball(aspect=R.aspect_of(W, H))]
 
         def frame():
@@ -427,8 +476,7 @@ def main():
             out = images.cpu().numpy()
         np.save(args.dump_images, out.reshape(F, -1))
 
-    t = torch.tensor([elapsed, float(rays), float(np.mean(kms)), float(cst.node_visits), float(cst.tri_tests),
-                      float(cst.hits), float(cst.rays)], dtype=torch.float64, device=dev)
+    t = torch.tensor([elapsed, float(rays)], dtype=torch.float64, device=dev)
     if world > 1:
         allv = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(allv, t)
@@ -439,22 +487,6 @@ def main():
     total_rays = float(allv[:, 1].sum())
 
     if rank == 0:
-        # roofline of the dominant kernel (the persistent render kernel) on rank 0's launches
-        pixels0 = int(max_local * BAND_ROWS * W) if b_count > 1 else W * H
-        bytes0 = algorithmic_bytes(cst, F * min(pixels0, W * H))
-        avg_ms = float(np.mean(kms))
-        achieved = bytes0 / (avg_ms * 1e-3) / 1e9
-        kname = st.kernel_name
-        sha = lib_sha()
-        pmc, pmc_src, pmc_med = None, "not measured (--no-pmc or N > 1)", {}
-        if world == 1 and not args.no_pmc and not args.resolution and not args.dragon_uv:
-            pmc, pmc_src, pmc_med = measure_pmc(args.config, F, kname)
-        if pmc is None and world == 1:  # the committed summary (one GPU's whole launch), same library build only
-            pmc_c, src_c = load_pmc(pmc_key(args.config, F), kname, sha)
-            if pmc_c is not None:
-                pmc, pmc_src = pmc_c, src_c
-            else:
-                pmc_src += f"; {src_c}"
         line = {
             "metric": METRIC,
             "value": total_rays / max_elapsed / 1e6,
@@ -483,21 +515,39 @@ def main():
                                      if bands and world > 1 else
                                      f"{world} GPU(s), {F} whole frame(s) per GPU per step, pixels stored in "
                                      "their images (setPixel layout)"),
-                       "scene_upload_s": round(upload_s, 4),
                        "scene_upload_first_s": round(upload_cold_s, 3),
-                       "scene_build": "GPU (rt_build.hip)" if build_info["gpu"] else "host (bvh_build.cpp)",
-                       "ub_regime_hits": {"hits": int(cst.hits), "ub": int(cst.ub_hits),
-                                          "share": (cst.ub_hits / cst.hits) if cst.hits else 0.0,
-                                          "note": "shaded triangle hits where the reference's barycentricCoordinates "
-                                                  "returns false (src/ray_tracing.cpp:281-295): rank 0's bands, "
-                                                  "counting pass"}},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": (float(pmc) if pmc is not None else None), "traffic_source": pmc_src,
-                         "kernel": kname, "lib_sha": sha, "source_hash": prov["library_source_hash"],
-                         "kernel_avg_ms": avg_ms,
-                         "algorithmic_bytes_per_launch": int(bytes0)},
+                       "scene_build": "GPU (rt_build.hip)" if build_info["gpu"] else "host (bvh_build.cpp)"},
+            "kernel": st.kernel_name if st is not None else None,
+            "source_hash": prov["library_source_hash"],
         }
+    if rank == 0 and args.full:  # everything below comes from runs of its own, beside the timed steps
+        # roofline of the dominant kernel (the persistent render kernel) on rank 0's launches
+        pixels0 = int(max_local * BAND_ROWS * W) if b_count > 1 else W * H
+        bytes0 = algorithmic_bytes(cst, F * min(pixels0, W * H))
+        avg_ms = float(np.mean(kms))
+        achieved = bytes0 / (avg_ms * 1e-3) / 1e9
+        kname = st.kernel_name
+        sha = lib_sha()
+        pmc, pmc_src, pmc_med = None, "not measured (--no-pmc or N > 1)", {}
+        if world == 1 and not args.no_pmc and not args.resolution and not args.dragon_uv:
+            pmc, pmc_src, pmc_med = measure_pmc(args.config, F, kname)
+        if pmc is None and world == 1:  # the committed summary (one GPU's whole launch), same library build only
+            pmc_c, src_c = load_pmc(pmc_key(args.config, F), kname, sha)
+            if pmc_c is not None:
+                pmc, pmc_src = pmc_c, src_c
+            else:
+                pmc_src += f"; {src_c}"
+        line["config"]["scene_upload_s"] = round(upload_s, 4)
+        line["config"]["ub_regime_hits"] = {
+            "hits": int(cst.hits), "ub": int(cst.ub_hits), "share": (cst.ub_hits / cst.hits) if cst.hits else 0.0,
+            "note": "shaded triangle hits where the reference's barycentricCoordinates returns false "
+                    "(src/ray_tracing.cpp:281-295): rank 0's bands, counting pass"}
+        line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": achieved / HBM_PEAK_GBS,
+                            "traffic": (float(pmc) if pmc is not None else None), "traffic_source": pmc_src,
+                            "kernel": kname, "lib_sha": sha, "source_hash": prov["library_source_hash"],
+                            "kernel_avg_ms": avg_ms,
+                            "algorithmic_bytes_per_launch": int(bytes0)}
         lane_use = {"node_steps": cdbg[1] / max(1, 64 * cdbg[4]), "record_steps": cdbg[2] / max(1, 64 * cdbg[5]),
                     "source": "counting pass of the same kernel (rt_debug_counters): lane visits / (64 x wave steps)"}
         if "SQ_INSTS_VALU" in pmc_med:
@@ -564,6 +614,7 @@ def main():
             whole = args.config in ("C1", "C2") and not args.cpu_pixels
             line["cpu_baseline"] = cpu_baseline(args.config, budget_s=480.0 if whole else args.cpu_budget,
                                                 max_pixels=args.cpu_pixels or None)
+    if rank == 0:
         print(json.dumps(line), flush=True)
     ctx.close()  # explicitly: no HIP teardown left to interpreter exit
     if ipc is not None and not ipc.owner:  # the importers unmap rank 0's images before rank 0 frees them

@@ -8,7 +8,7 @@
 #   tests[:PYTEST_K]            pytest -m gpu (optionally -k PYTEST_K)
 #   testsall                    pytest -m gpu without -x (every failure in one session; ends the session if any)
 #   smoke                       __graft_entry__.smoke()
-#   bench[:CFG[:VIEWS]]         bench.py line (N = 1; roofline.traffic measured by its rocprofv3 passes)
+#   bench[:CFG[:VIEWS]]         bench.py --full line (N = 1; roofline.traffic measured by its rocprofv3 passes)
 #   stats[:CFG[:VIEWS]]         rocprofv3 --kernel-trace --stats of bench.py (kernel summary for profiles/)
 #   kstats:CFG:VIEWS:OPTS:TAG2  rocprofv3 --kernel-trace --stats of tools/prof_target.py (OPTS k=v;k=v render options)
 #   pmcx:CFG:VIEWS:OPTS:TAG2:CTRS  one rocprofv3 --pmc pass (CTRS ;-separated) of tools/prof_target.py (OPTS k=v;k=v),
@@ -47,7 +47,7 @@ for step in "$@"; do
            run 1200 pytest_gpu_${TAG}.log python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread "${K[@]}" ;;
     testsall) run 1200 pytest_gpu_${TAG}.log python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread ;;
     smoke) run 300 smoke_${TAG}.log python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run 600 bench_${TAG}_${a:-C3}.json python bench.py --steps 20 --warmup 3 --config ${a:-C3} ${b:+--views $b} ;;
+    bench) run 600 bench_${TAG}_${a:-C3}.json python bench.py --full --steps 20 --warmup 3 --config ${a:-C3} ${b:+--views $b} ;;
     stats) run 600 stats_${TAG}_${a:-C3}.log rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/stats_${TAG}_${a:-C3} -o run -- python3 bench.py --steps 20 --warmup 3 --config ${a:-C3} ${b:+--views $b} --no-cpu-baseline --no-single-frame --no-pmc
            find gpurun_out/stats_${TAG}_${a:-C3} -name "*kernel_stats.csv" -exec head -3 {} \; ;;
     kstats) run 300 kstats_${TAG}_${d:-x}.log env PT_OPTS="${c//;/,}" rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/kstats_${TAG}_${d:-x} -o run -- python3 tools/prof_target.py ${a:-C3} 3 ${b:-64}
@@ -61,7 +61,7 @@ for step in "$@"; do
     simd)  c=${c//,/ }; run 300 simd_${TAG}_${a:-C3}.log env SE_VIEWS=${b:-16} python tools/simd_eff.py ${a:-C3} ${c//@/:} ;;
     wave)  run 300 wave_${TAG}${c:+_count}.log env WT_VIEWS=${b:-1} WT_COUNT=${c:-0} python tools/wave_trace.py ${a:-C3} ;;
     jobs)  run 300 jobs_${TAG}${b:+_$b}.log python tools/job_trace.py ${a:-C3} ${b//;/ } ;;
-    ranks) run 600 ranks_${TAG}.json env BENCH_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29555 bench.py --gpus 2 --steps 5 --warmup 1 --no-single-frame ;;
+    ranks) run 600 ranks_${TAG}.json env BENCH_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29555 bench.py --full --gpus 2 --steps 5 --warmup 1 --no-single-frame ;;
     ranksv) run 600 ranks_${TAG}_v${a:-96}.json env BENCH_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29556 bench.py --gpus 2 --steps 3 --warmup 1 --no-single-frame --no-pmc --no-cpu-baseline --views ${a:-96} ;;
     ipc)   run 150 ipc_${TAG}_v${a:-96}.log python -u tools/ipc_probe.py --views ${a:-96} --timeout 110 ;;
     phases) run 200 phases_${TAG}_${a:-C3}_${b:-1}.log python -u tools/phase_trace.py ${a:-C3} ${b:-1} ${c:-6} ;;
