@@ -949,6 +949,7 @@ int oracle_bvh_children(oracle_scene* o, int node, int* out, int cap) {
 }
 
 int oracle_intersect(oracle_scene* o, const rt_ray* rays, int n, int use_bvh, rt_hit* out) {
+#pragma omp parallel for schedule(dynamic, 16)  // (independent rays, as in oracle_shade)
     for (int i = 0; i < n; ++i) {
         Ray r;
         r.origin = V3::of(rays[i].origin);

@@ -1,5 +1,8 @@
-// rt_build.hip -- rt_create's acceleration structures built on the GPU (scenes of >= 65536
-// triangles; smaller scenes and every fallback use the host builders of bvh_build.cpp):
+// rt_build.hip -- rt_create's acceleration structures built on the GPU.  By default (build mode 0)
+// scenes of >= 65536 triangles (RT_GPU_BUILD_MIN) are built here and smaller ones by the host builders
+// of bvh_build.cpp; a forced build (rt_set_build_mode(2)) takes any scene of >= 16 triangles.  A scene
+// this file declines (gpu_build returns false) is built on the host in mode 0 and fails rt_create
+// in forced mode:
 //
 //   1. the reference's depth-4 median BVH (src/bounding_volume_hierarchy.cpp:108-366): four stable
 //      radix sorts of (segment, attribute) over all objects give its leaf order, from which each
