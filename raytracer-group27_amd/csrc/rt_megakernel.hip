@@ -18,6 +18,8 @@
 //                         one triangle record per iteration; lanes whose query completes park until
 //                         enough of the wave waits, then the wave advances them together.
 
+#include "kernel_plan.h"  // the RT_V_* variant bits
+
 namespace rt {
 
 enum LType { L_POINT = 0, L_SPHERE = 1, L_SPOT = 2, L_PLANE = 3, L_DONE = 4 };
@@ -1003,22 +1005,8 @@ __device__ __attribute__((noinline)) bool advance_lane_call(const void* ka, Lane
     return advance_lane<COUNT, TEX>(kernel_params(ka), kernel_jobs(ka), ka, L, fr, hit, b, fan, q, cnt, job_rays);
 }
 
-// Kernel variants (compile-time): bit 0 RT_V_CALL = state machine (and drain lane groups) out of line;
-// bit 1 RT_V_NOPF = no node prefetch in the dynamic-fetch traversal; bit 2 RT_V_NOCOOP = no drain lane
-// groups; bit 4 RT_V_W4 = compiled for 4 waves per SIMD (128 VGPRs) instead of 2 (256); bit 8 RT_V_FAN =
-// light-sample fans.  Every variant renders the same bits; they differ in registers, spills and occupancy.
-#define RT_V_CALL 1
-#define RT_V_NOPF 2
-#define RT_V_NOCOOP 4
-#define RT_V_W4 16  // compiled for 4 waves per SIMD (128 VGPRs)
-#define RT_V_FAN 256  // dynamic fetch: the spherical-light sample fans compiled in (P.fan)
-
-#define RT_V_W3 8    // compiled for 3 waves per SIMD (168 VGPRs)
-#define RT_V_REVISIT 32  // opaque / tree kernels: the re-visit group stack of the other kernels (A/B), not DIRECT
-#define RT_V_CHK 64      // tree kernel: the checked build (indices validated and reported, chk_report)
-#define RT_V_SPLIT 128   // opaque kernel: a node's shadow segment traced beside its mirror child (split_node)
-#define RT_V_W5 512      // opaque kernel: compiled for 5 waves per SIMD (96 VGPRs; with NOCOOP its LDS fits 20 blocks)
-#define RT_V_WAVES(V) (((V) & RT_V_W5) ? 5 : ((V) & RT_V_W4) ? 4 : ((V) & RT_V_W3) ? 3 : 2)
+// Kernel variants (compile-time, template parameter V): the RT_V_* bits of kernel_plan.h.  Every variant renders the
+// same bits; they differ in registers, spills and occupancy.
 
 // the ray mix of counting builds: a query starts (a cansee segment or light sample, or a camera ray: level 0, not a
 // segment) and ends (a camera ray that found nothing)

@@ -24,6 +24,7 @@
 
 #include "../../include/rt_amd.h"
 #include "bvh_build.h"
+#include "kernel_plan.h"
 #include "rt_build.h"
 #include "rt_internal.h"
 #include "rt_kernels.hip"
@@ -32,10 +33,7 @@
 
 using namespace rt;
 
-// dynamic-fetch kernel below this many triangles only when forced (RT_OPT_KERNEL): a query on a small
-// scene is a handful of node visits and the per-step refill bookkeeping does not pay (measured on
-// MI355X, DESIGN.md section 6: C1/C2/C5 vs C3/C4)
-#define RT_DF_MIN_TRIANGLES 65536
+#define RT_KERNEL_ENTRIES 35  // compiled megakernel instances (kernel_table)
 // scenes from this many triangles build their structures on the GPU (rt_build.hip); smaller ones, and
 // any scene the GPU path declines, on the host (bvh_build.cpp)
 #define RT_GPU_BUILD_MIN 65536
@@ -105,9 +103,7 @@ struct rt_ctx {
     int bvh8_depth = 0;
     bool df_ok = true;  // the BVH8 fits the dynamic-fetch kernel's LDS stack
     bool glossy_material = false;  // opaque, ks > 0, shininess != 0 (glossy_ray_count > 1 draws lobes)
-    int persistent_blocks[1024] = {0};  // resident 64-lane blocks per (kernel class, variant)
-    int opaque_blocks[6] = {0, 0, 0, 0, 0, 0};  // ... of the opaque-scene kernel (4 / 3 waves per SIMD; SPLIT; A/Bs)
-    int tree_blocks[4] = {0, 0, 0, 0};  // ... of the recursion-tree kernel (3-wave, re-visit, checked 4-wave, 4-wave)
+    int kernel_blocks[RT_KERNEL_ENTRIES] = {0};  // resident 64-lane blocks per kernel_table entry
     // recursion-tree kernel: the lanes' pending refracted rays (KParams::frames)
     float* d_frames = nullptr;
     float4* d_plane_tab = nullptr;  // plane lights: their sample grids and normals (KParams::plane_tab)
@@ -138,8 +134,8 @@ struct rt_ctx {
     int opt_fan_cap = 0;      // pixels a wave may have waiting on fans before it stops taking new ones (0: default)
     int opt_dual = -1;        // dynamic-fetch steps: record and node visit in one iteration (-1 default, 0 off, 1 on)
     int opt_variant = -1;   // -1: the shipped variant for the render shape (RT_DF_BATCH / _FRAME, RT_WT_DEFAULT)
-    int opt_opaque = -1;    // opaque-scene kernel: -1 where eligible (4-wave build), 0 never, 1 4-wave, 2 3-wave, 3 re-visit A/B
-    int opt_tree = -1;      // recursion-tree kernel: -1 / 2 where eligible, 0 never, 1 its re-visit group stack build (A/B)
+    int opt_opaque = -1;    // opaque-scene kernel: -1 where eligible, 0 never, 1..7 one of its builds (kernel_plan.h)
+    int opt_tree = -1;      // recursion-tree kernel: -1 / 2 where eligible, 0 never, 1 / 3 / 4 / 5 one of its builds
     char last_kernel[64] = {0};
     // view batches: the camera table's pinned host staging and the event of its last copy (the buffer
     // is refilled only once that copy has read it)
@@ -1031,273 +1027,94 @@ extern "C" int rt_ctx_set_option(rt_ctx* c, int option, int value) {
 }
 
 
-// lights whose samples the dynamic-fetch kernel traces as wave-shared fans pay for that kernel on a
-// small scene too: at least 16 and at most 64 samples per spherical or plane light (C5, 3 plane lights of
-// 8 x 8 with a glass sphere: single frame 813 -> 351 ms, 4-view batch 218 -> 204 ms/frame)
-static bool fans_pay(const rt_ctx* c, const KParams& K) {
-    if (!c->opt_fan) return false;
-    const int ns = K.S.nsl > 0 ? 1 + K.sl_m * K.sl_n : 0, np = K.S.nplane > 0 ? K.plane_k * K.plane_k : 0;
-    return (ns >= 16 && ns <= 64) || (np >= 16 && np <= 64);
+// Every compiled megakernel instance (kernel_plan.h names the builds): a render launches its plan's entry and sizes
+// its persistent grid by it; a plan without an entry is an error.
+struct KernelEntry {
+    int cls, variant;
+    bool count, tex;
+    void (*fn)(KParams, JobSrc);
+};
+// every build of the opaque and tree kernels plain and counting; the shipped variants of the general kernels plain,
+// textured and counting (counting builds keep the texture code: one instance each); the A/B alternate plain only
+#define RT_LITE_ROWS(CLS, KERNEL, V) {CLS, V, false, false, KERNEL<false, V>}, {CLS, V, true, false, KERNEL<true, V>}
+#define RT_SHIPPED_ROWS(CLS, KERNEL, V)                                                          \
+    {CLS, V, false, false, KERNEL<false, false, V>}, {CLS, V, false, true, KERNEL<false, true, V>}, \
+        {CLS, V, true, true, KERNEL<true, true, V>}
+static const KernelEntry kernel_table[] = {
+    RT_LITE_ROWS(KC_OPAQUE, persistent_opaque_kernel, RT_OPAQUE_V),
+    RT_LITE_ROWS(KC_OPAQUE, persistent_opaque_kernel, RT_OPAQUE_V | RT_V_REVISIT),  // A/B: the re-visit group stack
+    RT_LITE_ROWS(KC_OPAQUE, persistent_opaque_kernel, RT_OPAQUE_V3),
+    RT_LITE_ROWS(KC_OPAQUE, persistent_opaque_kernel, RT_OPAQUE_V | RT_V_SPLIT),
+    RT_LITE_ROWS(KC_OPAQUE, persistent_opaque_kernel, RT_OPAQUE_V3 | RT_V_SPLIT),
+    RT_LITE_ROWS(KC_OPAQUE, persistent_opaque_kernel, RT_OPAQUE_V5S),
+    RT_LITE_ROWS(KC_OPAQUE, persistent_opaque_kernel, RT_OPAQUE_V4SN),
+    RT_LITE_ROWS(KC_TREE, persistent_tree_kernel, RT_TREE_V3),
+    RT_LITE_ROWS(KC_TREE, persistent_tree_kernel, RT_TREE_VR),
+    RT_LITE_ROWS(KC_TREE, persistent_tree_kernel, RT_TREE_V4C),
+    RT_LITE_ROWS(KC_TREE, persistent_tree_kernel, RT_TREE_V4),
+    RT_SHIPPED_ROWS(KC_DF, persistent_df_kernel, RT_DF_BATCH),
+    RT_SHIPPED_ROWS(KC_DF, persistent_df_kernel, RT_DF_BATCH | RT_V_FAN),
+    RT_SHIPPED_ROWS(KC_DF, persistent_df_kernel, RT_DF_FRAME),
+    {KC_DF, RT_DF_ALT, false, false, persistent_df_kernel<false, false, RT_DF_ALT>},
+    RT_SHIPPED_ROWS(KC_WHOLE, persistent_kernel, RT_WT_DEFAULT),
+};
+static_assert(sizeof(kernel_table) / sizeof(kernel_table[0]) == RT_KERNEL_ENTRIES, "rt_ctx::kernel_blocks: one per entry");
+
+static const KernelEntry* find_kernel(int cls, int variant, bool count, bool tex) {
+    for (const KernelEntry& e : kernel_table)
+        if (e.cls == cls && e.variant == variant && e.count == count && e.tex == tex) return &e;
+    set_error("kernel variant not compiled for this render (counting and textured renders: shipped variants only)");
+    return nullptr;
 }
 
-// the scene's pixels can be drawn by the opaque-scene or the recursion-tree kernel (opaque_path / tree_path
-// without the class test): no textures, no glossy lobes, sample fans within a wave
-static bool lite_eligible(const rt_ctx* c, const KParams& K) {
-    if (c->opt_variant >= 0 || K.S.tex_on || !(K.glossy_n == 1 || !c->glossy_material)) return false;
-    const bool opaque = c->opt_opaque != 0 && K.S.all_opaque && K.S.nsl == 0 && K.S.nplane == 0;
-    const bool tree = c->opt_tree != 0 && c->opt_fan && (K.S.nsl == 0 || 1 + K.sl_m * K.sl_n <= 64) &&
-                      (K.S.nplane == 0 || K.plane_k * K.plane_k <= 64) &&
-                      (long long)K.S.npl + K.S.nsl + K.S.nspot + K.S.nplane < 65536;
-    return opaque || tree;
+// the launch's plan (kernel_plan.h), computed once per launch from the filled KParams: pixel work or rt_shade's rays
+static KernelPlan plan_of(const rt_ctx* c, const KParams& K, bool pixels, bool count) {
+    PlanInput in{};
+    in.ntri = c->ntri;
+    in.df_ok = c->df_ok;
+    in.glossy_material = c->glossy_material;
+    in.all_opaque = K.S.all_opaque;
+    in.npl = K.S.npl;
+    in.nsl = K.S.nsl;
+    in.nspot = K.S.nspot;
+    in.nplane = K.S.nplane;
+    in.tex_on = K.S.tex_on;
+    in.glossy_n = K.glossy_n;
+    in.sl_m = K.sl_m;
+    in.sl_n = K.sl_n;
+    in.plane_k = K.plane_k;
+    in.max_level = K.max_level;
+    in.n_views = K.n_views;
+    in.n_local_bands = K.n_local_bands;
+    in.band_rows = K.band_rows;
+    in.H = K.H;
+    in.pixels = pixels;
+    in.count = count;
+    in.opt_kernel = c->opt_kernel;
+    in.opt_variant = c->opt_variant;
+    in.opt_opaque = c->opt_opaque;
+    in.opt_tree = c->opt_tree;
+    in.opt_fan = c->opt_fan;
+    return plan_kernel(in);
 }
 
-// the kernel class a render runs: dynamic fetch for large scenes, sample-heavy lights and every scene the opaque or
-// recursion-tree kernel draws (round 6: C2 64-view batch 0.268 -> 0.109 ms/frame, frame 0.626 -> 0.38-0.50 ms;
-// profiles/r06/ab_r06e.log); whole-traversal refill for the small scenes left (textures, glossy lobes)
-static bool use_df(const rt_ctx* c, const KParams& K) {
-    if (!c->df_ok || c->opt_kernel == RT_KERNEL_WHOLE_TRAVERSAL) return false;
-    if (c->opt_kernel == RT_KERNEL_DYNAMIC_FETCH) return true;
-    return c->ntri >= RT_DF_MIN_TRIANGLES || fans_pay(c, K) || lite_eligible(c, K);
+static void launch_persistent(rt_ctx* c, const KernelEntry& e, const KernelPlan& P, int grid, hipStream_t st,
+                              const KParams& K, const JobSrc& J) {
+    hipLaunchKernelGGL(e.fn, dim3(grid), dim3(64), 0, st, K, J);
+    std::memcpy(c->last_kernel, P.name, sizeof(c->last_kernel));
 }
 
-// Kernel variants compiled (rt_megakernel.hip RT_V_*).  The dynamic-fetch class ships two, chosen by
-// render shape: view batches run the lean 4-waves-per-SIMD variant (state machine
-// out of line, no node prefetch, no drain lane groups: C3 16 views 0.785 ms/frame vs 0.907 at 3 waves,
-// 0.99 at 5, 1.11 for the 2-wave frame variant; C4 14.96 vs 17.8 / 18.7 / 24.1 ms/frame), single
-// frames the 2-wave variant with the drain lane groups (their tail dominates: C3 2.16-2.19 vs
-// 2.29-2.67 ms).  The whole-traversal class (small scenes) keeps the inline 2-wave variant (C2 0.76 vs
-// 0.81 ms, C5 742 vs 804 ms).  The alternates are kept for A/B measurement (RT_OPT_VARIANT); all
-// render identical bits.
-#define RT_DF_BATCH (RT_V_CALL | RT_V_NOPF | RT_V_NOCOOP | RT_V_W4)
-#define RT_DF_FRAME 0
-#define RT_WT_DEFAULT 0
-// the one A/B alternate: the batch variant with the drain lane groups, called out of line
-#define RT_DF_ALT (RT_V_CALL | RT_V_NOPF | RT_V_W4)
-// the opaque-scene kernel (rt_megakernel.hip persistent_opaque_kernel): 4 waves per SIMD
-// by render shape: view batches at 4 waves per SIMD (C3 64 views 0.558 vs 0.573 ms/frame at 3), single frames at
-// 3 (their tail is a few waves' serial chains, which run faster with more registers: 1.40-1.45 vs 1.56-1.63 ms)
-#define RT_OPAQUE_V (RT_V_W4 | RT_V_NOPF)
-#define RT_OPAQUE_V3 (RT_V_W3 | RT_V_NOPF)
-
-// Renders that the opaque-scene kernel draws: pixels (not rt_shade's explicit rays) of a large scene
-// (the dynamic-fetch class) whose materials are all opaque, lit by point and spot lights only, without
-// textures and without glossy lobes (glossy_ray_count 1, or no glossy material).  RT_OPT_OPAQUE 0 and any
-// RT_OPT_VARIANT choice select the general kernels instead.
-static bool use_df(const rt_ctx* c, const KParams& K);
-static bool split_ok(const KParams& K);
-static bool opaque_path(const rt_ctx* c, const KParams& K, bool pixels) {
-    // (small scenes with more than one light: the recursion-tree kernel draws them faster -- C2 64-view batch 0.104
-    // vs 0.100 ms/frame, frame 0.459 vs 0.376 ms, profiles/r06/ab_r06m.log -- unless RT_OPT_OPAQUE asks for it)
-    if (c->opt_opaque < 0 && c->ntri < RT_DF_MIN_TRIANGLES && !split_ok(K)) return false;
-    return pixels && c->opt_opaque != 0 && c->opt_variant < 0 && use_df(c, K) && K.S.all_opaque && K.S.nsl == 0 &&
-           K.S.nplane == 0 && !K.S.tex_on && (K.glossy_n == 1 || !c->glossy_material);
-}
-// the opaque kernel's build: 4 waves per SIMD for batches and single frames (round 4, with the direct group stack
-// and the leaf bound 2: C3 frame 1.237 vs 1.246 ms at 3 waves, profiles/r04/ab_r04g_refill.log), with SPLIT (a
-// node's shadow segment traced beside its mirror child, rt_megakernel.hip split_node) where the scene has one
-// light (point or spot) and at most 16 levels (the LDS result bits): its lane keeps 3 dwords between phases, so
-// the 4-wave build has no spills (31 VGPRs before) -- C3 64-view batch 0.376-0.378 -> 0.373 ms/frame, frame
-// 1.045-1.074 -> 0.95-0.97 ms (profiles/r05/ab_r05m.log, ab_r05n.log).  RT_OPT_OPAQUE 1 the 4-wave build without
-// SPLIT, 2 the 3-wave build, 3 the 4-wave re-visit A/B, 4 / 5 SPLIT at 4 / 3 waves, 6 / 7 SPLIT without the
-// drain lane groups at 5 / 4 waves (A/Bs: 0.388 / 0.377 ms/frame, frames 1.26 / 1.14 ms)
-#define RT_OPAQUE_V5S (RT_V_W5 | RT_V_NOPF | RT_V_NOCOOP | RT_V_SPLIT)   // A/B: 5 waves, no drain lane groups
-#define RT_OPAQUE_V4SN (RT_V_W4 | RT_V_NOPF | RT_V_NOCOOP | RT_V_SPLIT)  // A/B: 4 waves, no drain lane groups
-static bool split_ok(const KParams& K) { return K.S.npl + K.S.nspot == 1 && K.max_level < 16; }
-#define RT_V5_MIN_FRAMES 13.0
-static int opaque_variant(const rt_ctx* c, const KParams& K) {
-    // launches of at least RT_V5_MIN_FRAMES frames' worth of pixels with SPLIT: 5 waves per SIMD without the drain
-    // lane groups (round 6, every automatic variable defined: 20 spilled VGPRs instead of 33; C3 64-view batch 0.372
-    // -> 0.352 ms/frame, profiles/r06/ab_r06m.log).  Its per-launch drain is longer: the views fit is 0.334 + 1.128 /
-    // frames ms/frame against the 4-wave build's 0.3625 + 0.766 / frames (views_r06.log, views_r05fb.log), so the
-    // builds cross at ~13 frames' worth -- a band-split launch at N = 8 GPUs (64 views x 1/8 of each frame) keeps
-    // the 4-wave build with the lane groups, and so do single frames (1.13 vs 0.92 ms without them)
-    const double frames = (double)std::max(1, K.n_views) * K.n_local_bands * K.band_rows / std::max(1, K.H);
-    if (c->opt_opaque == -1 && frames >= RT_V5_MIN_FRAMES && split_ok(K)) return RT_OPAQUE_V5S;
-    if (c->opt_opaque == 2) return RT_OPAQUE_V3;
-    if (c->opt_opaque == 3) return RT_OPAQUE_V | RT_V_REVISIT;
-    if (c->opt_opaque == 1 || !split_ok(K)) return RT_OPAQUE_V;
-    if (c->opt_opaque == 6) return RT_OPAQUE_V5S;
-    if (c->opt_opaque == 7) return RT_OPAQUE_V4SN;
-    return (c->opt_opaque == 5 ? RT_OPAQUE_V3 : RT_OPAQUE_V) | RT_V_SPLIT;
-}
-
-// the recursion-tree kernel (rt_megakernel.hip persistent_tree_kernel): 4 / 3 waves per SIMD
-// View batches run the 4-wave build, single frames the 3-wave one (round 6: C4 16-view batch 6.77-6.82 -> 6.09-6.13
-// ms/frame, C4 frame 6.92-6.95 vs 7.32-7.57 ms at 4 waves; profiles/r06/ab_r06k*.log).  The 4-wave build faulted
-// in rounds 4-5 when compiled with undef values in its IR; with every automatic variable defined (build.py
-// HIP_FLAGS) it runs every size bit-identically.
-#define RT_TREE_V3 (RT_V_W3 | RT_V_NOPF)
-#define RT_TREE_VR (RT_V_W3 | RT_V_NOPF | RT_V_REVISIT)  // A/B: the re-visit group stack (RT_OPT_TREE 1)
-// developer diagnosis of the 4-wave build's fault (RT_OPT_TREE 3): that build with every index checked (RT_V_CHK)
-#define RT_TREE_V4C (RT_V_W4 | RT_V_NOPF | RT_V_CHK)
-#define RT_TREE_V4 (RT_V_W4 | RT_V_NOPF)  // launches of >= 6 frames (RT_OPT_TREE 4 forces it, 5 the 3-wave build)
-#define RT_TREE_V4_MIN_FRAMES 6.0
-
-// Renders that the recursion-tree kernel draws: pixels of a dynamic-fetch-class render the opaque kernel
-// does not take, without textures or glossy lobes, whose spherical and plane lights fit one fan (<= 64
-// samples; fans on).  RT_OPT_TREE 0 and any RT_OPT_VARIANT choice select the general kernels instead.
-static bool tree_path(const rt_ctx* c, const KParams& K, bool pixels) {
-    if (!pixels || c->opt_tree == 0 || c->opt_variant >= 0 || !c->opt_fan || !use_df(c, K) || opaque_path(c, K, pixels))
-        return false;
-    if (K.S.tex_on || !(K.glossy_n == 1 || !c->glossy_material)) return false;
-    if (K.S.nsl > 0 && 1 + K.sl_m * K.sl_n > 64) return false;
-    if (K.S.nplane > 0 && K.plane_k * K.plane_k > 64) return false;
-    return (long long)K.S.npl + K.S.nsl + K.S.nspot + K.S.nplane < 65536;  // TreeLane::li
-}
-static int tree_variant(const rt_ctx* c, const KParams& K) {
-    if (c->opt_tree == 1) return RT_TREE_VR;
-    if (c->opt_tree == 3) return RT_TREE_V4C;
-    if (c->opt_tree == 4) return RT_TREE_V4;
-    if (c->opt_tree == 5) return RT_TREE_V3;
-    // by frames' worth of pixels per launch, as the opaque kernel's builds: C4 16 views over 8 / 4 / 2 GPUs' band
-    // shares (2 / 4 / 8 frames) 2.17 / 2.53 / 3.96 ms/frame at 3 waves vs 2.29 / 2.57 / 3.62 at 4; C2 64 views
-    // over 8 GPUs (8 frames) 0.017 vs 0.016 (profiles/r06/ab_r06v_*.log)
-    const double frames = (double)std::max(1, K.n_views) * K.n_local_bands * K.band_rows / std::max(1, K.H);
-    return frames >= RT_TREE_V4_MIN_FRAMES ? RT_TREE_V4 : RT_TREE_V3;
-}
-
-// by render shape: view batches and sample-fan renders run the lean 4-wave variant (C4 single frame
-// with fans: 27.1 vs 30.3 ms), other single frames the 2-wave variant with the drain lane groups
-static int variant_of(const rt_ctx* c, bool df, const KParams& K) {
-    if (!df) return c->opt_variant >= 0 ? c->opt_variant : RT_WT_DEFAULT;
-    const int v = c->opt_variant >= 0 ? c->opt_variant : ((K.n_views > 1 || K.fan) ? RT_DF_BATCH : RT_DF_FRAME);
-    return K.fan ? (v | RT_V_FAN) : v;  // shape_options keeps K.fan to variants compiled with fans
-}
-
-template <bool DF, bool COUNT, bool TEX, int V>
-static void launch_v(int grid, hipStream_t st, const KParams& K, const JobSrc& J) {
-    if constexpr (DF)
-        hipLaunchKernelGGL((persistent_df_kernel<COUNT, TEX, V>), dim3(grid), dim3(64), 0, st, K, J);
-    else
-        hipLaunchKernelGGL((persistent_kernel<COUNT, TEX, V>), dim3(grid), dim3(64), 0, st, K, J);
-}
-
-// every (COUNT, TEX) instance of the shipped variants; the A/B alternates plain only
-template <bool COUNT, bool TEX>
-static bool launch_shipped(bool df, int v, int grid, hipStream_t st, const KParams& K, const JobSrc& J) {
-    if (df && v == RT_DF_BATCH) launch_v<true, COUNT, TEX, RT_DF_BATCH>(grid, st, K, J);
-    else if (df && v == (RT_DF_BATCH | RT_V_FAN)) launch_v<true, COUNT, TEX, RT_DF_BATCH | RT_V_FAN>(grid, st, K, J);
-    else if (df && v == RT_DF_FRAME) launch_v<true, COUNT, TEX, RT_DF_FRAME>(grid, st, K, J);
-    else if (!df && v == RT_WT_DEFAULT) launch_v<false, COUNT, TEX, RT_WT_DEFAULT>(grid, st, K, J);
-    else return false;
-    return true;
-}
-
-template <bool COUNT>
-static int launch_persistent(int grid, hipStream_t st, const KParams& K, const JobSrc& J, rt_ctx* c) {
-    if (opaque_path(c, K, J.mode == 0)) {
-        const int v = opaque_variant(c, K);
-        if (v == (RT_OPAQUE_V | RT_V_REVISIT)) {  // A/B: the 4-wave build with the re-visit group stack
-            hipLaunchKernelGGL((persistent_opaque_kernel<COUNT, RT_OPAQUE_V | RT_V_REVISIT>), dim3(grid), dim3(64), 0, st,
-                               K, J);
-        } else if (v == RT_OPAQUE_V3) {
-            hipLaunchKernelGGL((persistent_opaque_kernel<COUNT, RT_OPAQUE_V3>), dim3(grid), dim3(64), 0, st, K, J);
-        } else if (v == (RT_OPAQUE_V | RT_V_SPLIT)) {
-            hipLaunchKernelGGL((persistent_opaque_kernel<COUNT, RT_OPAQUE_V | RT_V_SPLIT>), dim3(grid), dim3(64), 0, st, K, J);
-        } else if (v == (RT_OPAQUE_V3 | RT_V_SPLIT)) {
-            hipLaunchKernelGGL((persistent_opaque_kernel<COUNT, RT_OPAQUE_V3 | RT_V_SPLIT>), dim3(grid), dim3(64), 0, st, K, J);
-        } else if (v == RT_OPAQUE_V5S) {
-            hipLaunchKernelGGL((persistent_opaque_kernel<COUNT, RT_OPAQUE_V5S>), dim3(grid), dim3(64), 0, st, K, J);
-        } else if (v == RT_OPAQUE_V4SN) {
-            hipLaunchKernelGGL((persistent_opaque_kernel<COUNT, RT_OPAQUE_V4SN>), dim3(grid), dim3(64), 0, st, K, J);
-
-        } else {
-            hipLaunchKernelGGL((persistent_opaque_kernel<COUNT, RT_OPAQUE_V>), dim3(grid), dim3(64), 0, st, K, J);
-        }
-        std::snprintf(c->last_kernel, sizeof(c->last_kernel), "rt::persistent_opaque_kernel<%s, %d>",
-                      COUNT ? "true" : "false", v);
-        return RT_OK;
-    }
-    if (tree_path(c, K, J.mode == 0)) {
-        const int v = tree_variant(c, K);
-        if (v == RT_TREE_VR) hipLaunchKernelGGL((persistent_tree_kernel<COUNT, RT_TREE_VR>), dim3(grid), dim3(64), 0, st, K, J);
-        else if (v == RT_TREE_V4C) hipLaunchKernelGGL((persistent_tree_kernel<COUNT, RT_TREE_V4C>), dim3(grid), dim3(64), 0, st, K, J);
-        else if (v == RT_TREE_V4) hipLaunchKernelGGL((persistent_tree_kernel<COUNT, RT_TREE_V4>), dim3(grid), dim3(64), 0, st, K, J);
-        else hipLaunchKernelGGL((persistent_tree_kernel<COUNT, RT_TREE_V3>), dim3(grid), dim3(64), 0, st, K, J);
-        std::snprintf(c->last_kernel, sizeof(c->last_kernel), "rt::persistent_tree_kernel<%s, %d>",
-                      COUNT ? "true" : "false", v);
-        return RT_OK;
-    }
-    const bool df = use_df(c, K);
-    const bool tex = COUNT || K.S.tex_on;  // counting builds keep the texture code (one instance each)
-    const int v = variant_of(c, df, K);
-    bool ok = tex ? launch_shipped<COUNT, true>(df, v, grid, st, K, J) : launch_shipped<COUNT, false>(df, v, grid, st, K, J);
-    if (!ok && !COUNT && !tex) {
-        ok = true;
-        if (df && v == RT_DF_ALT) launch_v<true, false, false, RT_DF_ALT>(grid, st, K, J);
-        else ok = false;
-    }
-    if (!ok) {
-        set_error("kernel variant not compiled for this render (counting and textured renders: shipped variants only)");
-        return RT_ERR_INVALID;
-    }
-    // the name rocprofv3 lists for this launch (bench.py's roofline.kernel)
-    std::snprintf(c->last_kernel, sizeof(c->last_kernel), "rt::%s<%s, %s, %d>",
-                  df ? "persistent_df_kernel" : "persistent_kernel", COUNT ? "true" : "false", tex ? "true" : "false",
-                  v);
-    return RT_OK;
-}
-
-template <bool DF, int V>
-static int occupancy_of(int* per_cu) {
-    if constexpr (DF)
-        return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, persistent_df_kernel<false, false, V>, 64, 0);
-    else
-        return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, persistent_kernel<false, false, V>, 64, 0);
-}
-
-// resident 64-lane blocks of the kernel (the persistent grid)
-static int persistent_grid(rt_ctx* c, const KParams& K, bool pixels) {
-    if (opaque_path(c, K, pixels)) {
-        const int v = opaque_variant(c, K);
-        const int key = v == RT_OPAQUE_V5S ? 4 : v == RT_OPAQUE_V4SN ? 5 : ((v & RT_V_W3) ? 1 : 0) + ((v & RT_V_SPLIT) ? 2 : 0);
-        if (c->opaque_blocks[key] > 0) return c->opaque_blocks[key];
-        int cus = 0, per_cu = 0;
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-        const hipError_t e =
-            key == 5   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_opaque_kernel<false, RT_OPAQUE_V4SN>, 64, 0)
-            : key == 4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_opaque_kernel<false, RT_OPAQUE_V5S>, 64, 0)
-            : key == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_opaque_kernel<false, RT_OPAQUE_V3 | RT_V_SPLIT>, 64, 0)
-            : key == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_opaque_kernel<false, RT_OPAQUE_V | RT_V_SPLIT>, 64, 0)
-            : key == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_opaque_kernel<false, RT_OPAQUE_V3>, 64, 0)
-                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_opaque_kernel<false, RT_OPAQUE_V>, 64, 0);
-        if (e != hipSuccess || per_cu <= 0) per_cu = 8;
-        c->opaque_blocks[key] = std::max(1, cus) * per_cu;
-        return c->opaque_blocks[key];
-    }
-    if (tree_path(c, K, pixels)) {
-        const int tv = tree_variant(c, K);
-        const int key = tv == RT_TREE_VR ? 1 : tv == RT_TREE_V4C ? 2 : tv == RT_TREE_V4 ? 3 : 0;
-        if (c->tree_blocks[key] > 0) return c->tree_blocks[key];
-        int cus = 0, per_cu = 0;
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-        const hipError_t e =
-            key == 3   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_tree_kernel<false, RT_TREE_V4>, 64, 0)
-            : key == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_tree_kernel<false, RT_TREE_VR>, 64, 0)
-            : key == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_tree_kernel<false, RT_TREE_V4C>, 64, 0)
-                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_tree_kernel<false, RT_TREE_V3>, 64, 0);
-        if (e != hipSuccess || per_cu <= 0) per_cu = 8;
-        c->tree_blocks[key] = std::max(1, cus) * per_cu;
-        return c->tree_blocks[key];
-    }
-    const bool df = use_df(c, K);
-    const int v = variant_of(c, df, K);
-    const int key = (df ? 512 : 0) + (v & 511);
-    if (c->persistent_blocks[key] > 0) return c->persistent_blocks[key];
+// resident 64-lane blocks of the kernel (the persistent grid), by the occupancy of its plain build (the counting and
+// textured builds of a variant run the plain build's grid)
+static int persistent_grid(rt_ctx* c, const KernelEntry& e) {
+    const KernelEntry& plain = *find_kernel(e.cls, e.variant, false, false);  // every variant of the table has one
+    int& blocks = c->kernel_blocks[&plain - kernel_table];
+    if (blocks > 0) return blocks;
     int cus = 0, per_cu = 0;
     hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-    int e = 1;
-    if (df) {
-        if (v == RT_DF_BATCH) e = occupancy_of<true, RT_DF_BATCH>(&per_cu);
-        else if (v == (RT_DF_BATCH | RT_V_FAN)) e = occupancy_of<true, RT_DF_BATCH | RT_V_FAN>(&per_cu);
-        else if (v == RT_DF_FRAME) e = occupancy_of<true, RT_DF_FRAME>(&per_cu);
-        else e = occupancy_of<true, RT_DF_ALT>(&per_cu);
-    } else {
-        e = occupancy_of<false, RT_WT_DEFAULT>(&per_cu);
-    }
-    if (e != 0 || per_cu <= 0) per_cu = 8;
-    c->persistent_blocks[key] = std::max(1, cus) * per_cu;
-    return c->persistent_blocks[key];
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, plain.fn, 64, 0) != hipSuccess || per_cu <= 0) per_cu = 8;
+    blocks = std::max(1, cus) * per_cu;
+    return blocks;
 }
 
 static int fill_params(rt_ctx* c, const rt_camera* cam, const rt_params* p, int W, int H, KParams& K) {
@@ -1419,7 +1236,7 @@ static int fill_params(rt_ctx* c, const rt_camera* cam, const rt_params* p, int 
 
 // batches (n_views > 1) advance whole waves (C3, 8 views: refill 24 -> 64 = 1.59 -> 1.37 ms/frame)
 // with lane groups for the stragglers (16 views 1.29 -> 1.17 ms/frame); then the context's options
-static void shape_options(const rt_ctx* c, KParams& K) {
+static void shape_options(const rt_ctx* c, const KernelPlan& P, KParams& K) {
     if (K.n_views > 1) {
         K.refill = 64;
         K.coop = 2;
@@ -1437,17 +1254,14 @@ static void shape_options(const rt_ctx* c, KParams& K) {
     // spherical lights (bit 0) and plane lights (bit 1) as wave-shared fans (rt_megakernel.hip FanTable):
     // dynamic-fetch kernel, at most 64 samples per light (one mask); scenes with transparent materials
     // carry each sample's intensity
-    const bool sph_fans = K.S.nsl > 0 && 1 + K.sl_m * K.sl_n <= 64;
-    const bool plane_fans = K.S.nplane > 0 && K.plane_k * K.plane_k <= 64;
-    K.fan = (c->opt_fan && use_df(c, K)) ? ((sph_fans ? 1 : 0) | (plane_fans ? 2 : 0)) : 0;
-    if (c->opt_variant >= 0 && c->opt_variant != RT_DF_BATCH) K.fan = 0;  // fans are compiled into that variant only
+    K.fan = P.fan;
     K.fan_cap = c->opt_fan_cap > 0 ? c->opt_fan_cap : 16;
     // single frames with fans: a wave's jobs spread over 64 tiles (C4 52.9 -> 31.4 ms; the tile order
     // keeps its coherence elsewhere: C3 2.18 vs 2.41 ms, C2 0.77 vs 0.98 ms)
     // ... and single frames of the opaque-scene kernel over 16 tiles (4 pixels of each per wave; round 4, with the
     // direct group stack: C3 frame 1.06 ms vs 1.20 untouched, 1.14 over 64 tiles, profiles/r04/ab_r04n_interleave.log;
     // over 64 tiles it had lost in round 3, 1.41 vs 1.33)
-    const bool opq = opaque_path(c, K, true), opq_frame = K.n_views <= 1 && opq;
+    const bool opq = P.opaque_pixels, opq_frame = K.n_views <= 1 && opq;
     const int il = c->opt_interleave >= 0 ? c->opt_interleave : (opq_frame ? 4 : (K.fan && K.n_views <= 1 ? 1 : 0));
     K.interleave = il == 1 ? 6 : il;  // log2 of the tiles a wave's jobs spread over (option 1: 64 tiles)
     K.interleave_view = 0;
@@ -1460,13 +1274,34 @@ static void shape_options(const rt_ctx* c, KParams& K) {
     // single frames of the opaque-scene kernel start every XCD range at its rows nearest the image centre: the
     // frame's longest query chains (reflections inside the object) start first (C3 frame 1.40 -> 1.33 ms; the
     // 64-view batch and the fan renders, C4 / C5, gain nothing or lose: DESIGN.md section 6c)
-    K.centre_first = c->opt_centre_first >= 0 ? c->opt_centre_first : (K.n_views <= 1 && opaque_path(c, K, true) ? 1 : 0);
+    K.centre_first = c->opt_centre_first >= 0 ? c->opt_centre_first : (opq_frame ? 1 : 0);
     // fan renders advance whole waves: the fans keep a wave's free lanes busy, so waiting for all 64
     // costs little and each pass takes many new pixels (C4 single frame, refill 24 -> 64: 27.0 -> 13.2 ms)
     if (K.fan && c->opt_refill == 0) K.refill = 64;
     // (C3 16-view batch 0.81 -> 0.71 ms/frame, C4 single frame 13.1 -> 11.1 ms; a second record per
     // step for lanes without a node visit measured slower: 0.72 / 11.4)
     K.dual = c->opt_dual >= 0 ? c->opt_dual : 1;
+}
+
+// a launch's counters, kernel name and (timed: something ran between ev0 and ev1) kernel time; waits for the stream
+static int read_stats(rt_ctx* c, hipStream_t st, bool timed, rt_stats* stats) {
+    // (into pinned memory: a pageable destination stages the copy, ~10 us more per frame)
+    unsigned long long* h = c->h_stats;
+    HIP_TRY(hipMemcpyAsync(h, c->d_stats, 13 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::memset(stats, 0, sizeof(*stats));
+    stats->rays = h[0];
+    stats->node_visits = h[1];
+    stats->tri_tests = h[2];
+    stats->hits = h[3];
+    stats->ub_hits = h[12];
+    float ms = 0.0f;
+    if (timed) HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    stats->kernel_ms = ms;
+    stats->node_bytes = RT_NODE_DW * 4u;  // quantised BVH8 node
+    std::memcpy(stats->kernel, c->last_kernel, sizeof(stats->kernel));
+    stats->kernel[sizeof(stats->kernel) - 1] = 0;
+    return RT_OK;
 }
 
 // ---- the wavefront path (rt_wavefront.hip) ----
@@ -1480,8 +1315,8 @@ static void shape_options(const rt_ctx* c, KParams& K) {
 #define RT_WF_BUDGET (64ull << 30)  // bytes of queues and shading points per chunk of camera jobs (at most; and
                                     // at most a third of the free HBM)
 // -1 (the default) is the megakernel: no render shape measured faster on the wavefront path
-static bool wf_path(const rt_ctx* c, const KParams& K) {
-    if (c->opt_wavefront == 0 || !opaque_path(c, K, true) || K.aa || K.multi) return false;
+static bool wf_path(const rt_ctx* c, const KernelPlan& P, const KParams& K) {
+    if (c->opt_wavefront == 0 || !P.opaque_pixels || K.aa || K.multi) return false;
     if (K.S.npl + K.S.nspot > 32) return false;
     return c->opt_wavefront > 0;
 }
@@ -1629,33 +1464,16 @@ static int launch_wavefront(rt_ctx* c, KParams& K, hipStream_t st, rt_stats* sta
     }
     HIP_TRY(hipEventRecord(c->ev1, st));
     std::snprintf(c->last_kernel, sizeof(c->last_kernel), "rt::wf_trace_kernel<%s", COUNT ? "true" : "false");
-    if (stats) {
-        // (into pinned memory: a pageable destination stages the copy, ~10 us more per frame)
-        unsigned long long* h = c->h_stats;
-        HIP_TRY(hipMemcpyAsync(h, c->d_stats, 13 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        std::memset(stats, 0, sizeof(*stats));
-        stats->rays = h[0];
-        stats->node_visits = h[1];
-        stats->tri_tests = h[2];
-        stats->hits = h[3];
-        stats->ub_hits = h[12];
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        stats->kernel_ms = ms;
-        stats->node_bytes = RT_NODE_DW * 4u;
-        std::memcpy(stats->kernel, c->last_kernel, sizeof(stats->kernel));
-        stats->kernel[sizeof(stats->kernel) - 1] = 0;
-    }
-    return RT_OK;
+    return stats ? read_stats(c, st, true, stats) : RT_OK;
 }
 
 static int launch_render(rt_ctx* c, KParams& K, hipStream_t st, int count_mode, rt_stats* stats) {
     const int tiles_x = (K.W + 7) / 8;
     const int tiles_y = (K.band_rows + 7) / 8;
     const long long blocks = (long long)tiles_x * tiles_y * K.n_local_bands;
-    shape_options(c, K);
-    if (blocks > 0 && wf_path(c, K))
+    const KernelPlan plan = plan_of(c, K, true, count_mode != 0);
+    shape_options(c, plan, K);
+    if (blocks > 0 && wf_path(c, plan, K))
         return count_mode ? launch_wavefront<true>(c, K, st, stats) : launch_wavefront<false>(c, K, st, stats);
     c->wf_last_cnt = nullptr;
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, RT_STATS_BYTES, st));
@@ -1667,19 +1485,14 @@ static int launch_render(rt_ctx* c, KParams& K, hipStream_t st, int count_mode, 
         J.njobs = J.n_views * J.view_jobs;
         K.view_jobs = J.view_jobs;
         J.counter = reinterpret_cast<int*>(c->d_stats + 7);
-        J.xq = use_df(c, K) ? reinterpret_cast<int*>(c->d_stats + 16) : nullptr;
-        const int grid = (int)std::min<long long>(blocks * J.n_views, persistent_grid(c, K, true));
-        if (tree_path(c, K, true)) {
-            // the tree kernel's frame stacks: max_level frames of 48 B per resident lane
+        J.xq = plan.df() ? reinterpret_cast<int*>(c->d_stats + 16) : nullptr;
+        const KernelEntry* kern = find_kernel(plan.cls, plan.variant, plan.count, plan.tex);
+        if (!kern) return RT_ERR_INVALID;
+        const int grid = (int)std::min<long long>(blocks * J.n_views, persistent_grid(c, *kern));
+        if (plan.frame_bytes > 0) {
+            // the tree kernel's frame stacks and SPLIT's node frames, per resident lane
             const size_t slots = (size_t)grid * 64;
-            const int rc = ensure(c, &c->d_frames, &c->frames_bytes, slots * std::max(1, K.max_level) * 48);
-            if (rc != RT_OK) return rc;
-            K.frames = reinterpret_cast<float4*>(c->d_frames);
-            K.frame_slots = (int)slots;
-        } else if (opaque_path(c, K, true) && (opaque_variant(c, K) & RT_V_SPLIT)) {
-            // SPLIT: max_level + 1 node frames of 32 B per resident lane
-            const size_t slots = (size_t)grid * 64;
-            const int rc = ensure(c, &c->d_frames, &c->frames_bytes, slots * (K.max_level + 1) * 32);
+            const int rc = ensure(c, &c->d_frames, &c->frames_bytes, slots * plan.frame_bytes);
             if (rc != RT_OK) return rc;
             K.frames = reinterpret_cast<float4*>(c->d_frames);
             K.frame_slots = (int)slots;
@@ -1698,30 +1511,11 @@ static int launch_render(rt_ctx* c, KParams& K, hipStream_t st, int count_mode, 
             c->phase_trace_n = ph ? grid : 0;
         }
         HIP_TRY(hipEventRecord(c->ev0, st));
-        const int lrc = count_mode ? launch_persistent<true>(grid, st, K, J, c) : launch_persistent<false>(grid, st, K, J, c);
-        if (lrc != RT_OK) return lrc;
+        launch_persistent(c, *kern, plan, grid, st, K, J);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->ev1, st));
     }
-    if (stats) {
-        // (into pinned memory: a pageable destination stages the copy, ~10 us more per frame)
-        unsigned long long* h = c->h_stats;
-        HIP_TRY(hipMemcpyAsync(h, c->d_stats, 13 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        std::memset(stats, 0, sizeof(*stats));
-        stats->rays = h[0];
-        stats->node_visits = h[1];
-        stats->tri_tests = h[2];
-        stats->hits = h[3];
-        stats->ub_hits = h[12];
-        float ms = 0.0f;
-        if (blocks > 0) HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        stats->kernel_ms = ms;
-        stats->node_bytes = RT_NODE_DW * 4u;  // quantised BVH8 node
-        std::memcpy(stats->kernel, c->last_kernel, sizeof(stats->kernel));
-        stats->kernel[sizeof(stats->kernel) - 1] = 0;
-    }
-    return RT_OK;
+    return stats ? read_stats(c, st, blocks > 0, stats) : RT_OK;
 }
 
 static int g_count_mode = 0;  // set by rt_set_counting (counting build of the same kernel)
@@ -2128,7 +1922,8 @@ extern "C" int rt_shade(rt_ctx* c, const rt_ray* rays, int n, const rt_params* p
     KParams K;
     int rc = fill_params(c, nullptr, p, 1, 1, K);
     if (rc != RT_OK) return rc;
-    shape_options(c, K);
+    const KernelPlan plan = plan_of(c, K, false, g_count_mode != 0);
+    shape_options(c, plan, K);
     rt_ray* d_r = nullptr;
     float* d_c = nullptr;
     unsigned long long* d_n = nullptr;
@@ -2147,12 +1942,14 @@ extern "C" int rt_shade(rt_ctx* c, const rt_ray* rays, int n, const rt_params* p
         J.n_views = 1;
         J.view_jobs = n;
         J.counter = reinterpret_cast<int*>(c->d_stats + 7);
-        J.xq = use_df(c, K) ? reinterpret_cast<int*>(c->d_stats + 16) : nullptr;
-        const int grid = std::min((n + 63) / 64, persistent_grid(c, K, false));
-        const int lrc = g_count_mode ? launch_persistent<true>(grid, c->stream, K, J, c)
-                                     : launch_persistent<false>(grid, c->stream, K, J, c);
-        if (lrc != RT_OK) e = hipErrorInvalidValue;
-        else e = hipGetLastError();
+        J.xq = plan.df() ? reinterpret_cast<int*>(c->d_stats + 16) : nullptr;
+        const KernelEntry* kern = find_kernel(plan.cls, plan.variant, plan.count, plan.tex);
+        if (!kern) {
+            e = hipErrorInvalidValue;
+        } else {
+            launch_persistent(c, *kern, plan, std::min((n + 63) / 64, persistent_grid(c, *kern)), c->stream, K, J);
+            e = hipGetLastError();
+        }
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(rgb, d_c, sizeof(float) * 3 * n, hipMemcpyDeviceToHost);
