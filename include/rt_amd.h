@@ -19,7 +19,10 @@
  *   rt_render_device     same as rt_render, band-partitioned, device-resident output (multi-GPU path)
  *   rt_render_views_device  a batch of rt_render_device frames (one camera each) in one launch
  *   rt_render_views      the same batch, host output in the rt_render layout
+ *   rt_render_texture_views  renderRayTracing(..., textureDebugging = true): ViewMode::Textures,
+ *                        getFinalColorNoRayTracingJustTextures, src/main.cpp:76-109,355-356,752-761
  *   rt_camera_from_trackball  Trackball::generateRay / position(), framework/src/trackball.cpp:65-98
+ *   rt_camera_rays       Trackball::generateRay for every pixel of a frame (src/main.cpp:350-354)
  *   rt_scene_load_obj    std::vector<Mesh> loadMesh(path, bool normalize), src/mesh.cpp:58-188
  *   rt_scene_preset      Scene loadScene(SceneType, dataDir), src/scene.cpp:4-150
  *   rt_update_lights     the ImGui light editors after the BVH exists, src/main.cpp:511-613
@@ -276,6 +279,10 @@ int rt_write_dragon_proxy(const char* obj_path, int u_segments, int v_segments);
 int rt_camera_from_trackball(const float look_at[3], const float euler_radians[3], float distance,
                              float fovy_radians, float aspect, rt_camera* out);
 
+/* Trackball::generateRay for every pixel of a frame, host only (no device): rays_out[y*W + x], reference y
+ * (before the setPixel flip), t = FLT_MAX; the bits the kernels' gen_ray produces. */
+int rt_camera_rays(const rt_camera* cam, int width, int height, rt_ray* rays_out);
+
 /* ---- device context ---- */
 /* Number of visible HIP devices (initialises this library's HIP runtime); RT_ERR_NO_DEVICE (n = 0)
  * without a GPU.  In a process that also hosts PyTorch's bundled copy of the HIP runtime, let
@@ -340,6 +347,33 @@ int rt_render_views(rt_ctx* ctx, const rt_camera* cams, int n_views, const rt_pa
 int rt_render_views_image_device(rt_ctx* ctx, const rt_camera* cams, int n_views, const rt_params* params, int width,
                                  int height, int band_rows, int band_rank, int band_count, float* d_images,
                                  void* stream, rt_stats* stats);
+
+/*
+ * renderRayTracing(..., textureDebugging = true): ViewMode::Textures, src/main.cpp:76-109,355-356,752-761 --
+ * one camera ray per pixel, first hit only (rt::texture_view_kernel, no shading): a miss is (0,0,0), a triangle
+ * whose mesh has a kd texture is that texture's getPixel(texCoord, lod) under the params' texture_filtering /
+ * out_of_bounds rules / border colour (lod from the camera ray's differentials for the three mip filters),
+ * every other hit (spheres included: the reference declines their level of detail, and textures bind to
+ * meshes only) is (1,1,1).  The view samples whatever params->use_textures says, as the reference reads
+ * mat.kdTexture without looking at useTextures; anti_aliasing / multiple_rays are ignored, as there.  Of
+ * rt_params it reads texture_filtering, out_of_bounds_x/y, border_color and use_bvh.
+ * Outputs in the rt_render_views_image_device layout: view v's pixel (x, y) has its rgb at
+ * d_images[v*W*H*3 + ((H-1-y)*W + x)*3] and, where the pointers are not NULL, its first hit's primitive
+ * (rt_hit.prim_id: scene-order triangle, or num_triangles + sphere; -1 on a miss) and depth (ray.t; FLT_MAX
+ * on a miss) at d_prim / d_t[v*W*H + (H-1-y)*W + x].  Pixels outside the call's bands are not touched.  Same
+ * band arguments, validation, stream semantics and per-render scratch as rt_render_views_image_device.
+ * Multi-device contexts: when every replica stores straight into devices[0]'s images (rt_ctx_peer_stores all
+ * 1, and the outputs are not another process's rt_ipc_open mapping) the bands split over the devices as in
+ * rt_render_views_image_device, for all three outputs; otherwise the whole call runs on devices[0] (this view
+ * has no band-dense copy path).  stats: rays = pixels rendered, kernel_ms, node_bytes, kernel; zeros elsewhere.
+ */
+int rt_render_texture_views_image_device(rt_ctx* ctx, const rt_camera* cams, int n_views, const rt_params* params,
+                                         int width, int height, int band_rows, int band_rank, int band_count,
+                                         float* d_images, int32_t* d_prim, float* d_t, void* stream, rt_stats* stats);
+/* The same to host memory: rgb_out = n_views frames of W*H*3 floats (the rt_render_views layout), prim_out /
+ * t_out = n_views frames of W*H values or NULL. */
+int rt_render_texture_views(rt_ctx* ctx, const rt_camera* cams, int n_views, const rt_params* params,
+                            int width, int height, float* rgb_out, int32_t* prim_out, float* t_out, rt_stats* stats);
 
 /* Un-permute gathered band buffers ([band_count][max_local_bands][band_rows][W][3]) into the
  * setPixel layout on the device. */

@@ -659,11 +659,18 @@ inline vec3 getFinalColor(Scene& scene, const BoundingVolumeHierarchy& bvh, Ray 
 inline void renderRayTracing(Scene& scene, const Trackball& camera, const BoundingVolumeHierarchy& bvh, Screen& screen,
                              bool textureDebugging = false, bool anti_aliasing = false, bool multipleRays = false,
                              int sampleSize = 4) {
-    if (textureDebugging)  // getFinalColorNoRayTracingJustTextures (src/main.cpp:76-109): out of scope
-        throw std::runtime_error("renderRayTracing: the texture-debug view is not part of the GPU path");
     bvh.sync(scene);
     const rt_camera c = camera.camera();
     rt_params p = current_params();
+    if (textureDebugging) {
+        // ViewMode::Textures, getFinalColorNoRayTracingJustTextures per pixel (src/main.cpp:76-109,355-356): the
+        // first hit's texel or white; the reference ignores anti_aliasing / multipleRays in this view
+        check(rt_render_texture_views(bvh.handle(), &c, 1, &p, screen.width(), screen.height(),
+                                      screen.textureData().data(), nullptr, nullptr, nullptr),
+              "renderRayTracing(textureDebugging)");
+        screen.postprocessImage();
+        return;
+    }
     p.anti_aliasing = anti_aliasing ? 1 : 0;
     p.multiple_rays = multipleRays ? 1 : 0;
     p.sample_size = sampleSize;
@@ -689,6 +696,24 @@ inline void renderRayTracingViews(Scene& scene, const std::vector<Trackball>& ca
     std::vector<float> all(frame * cameras.size());
     check(rt_render_views(bvh.handle(), c.data(), (int)c.size(), &p, W, H, all.data(), nullptr),
           "renderRayTracingViews");
+    screens.assign(cameras.size(), {});
+    for (size_t v = 0; v < cameras.size(); ++v) screens[v].assign(all.begin() + v * frame, all.begin() + (v + 1) * frame);
+}
+
+// A batch of renderRayTracing(..., textureDebugging = true) calls, one per camera, in one launch
+// (rt_render_texture_views): screens[v] = the texture-debug frame of cameras[v], bit-identical to the single
+// call with that camera (before post-processing).
+inline void renderTextureViews(Scene& scene, const std::vector<Trackball>& cameras, const BoundingVolumeHierarchy& bvh,
+                               int W, int H, std::vector<std::vector<float>>& screens) {
+    bvh.sync(scene);
+    std::vector<rt_camera> c;
+    for (const Trackball& t : cameras) c.push_back(t.camera());
+    const rt_params p = current_params();
+    const size_t frame = (size_t)W * H * 3;
+    std::vector<float> all(frame * cameras.size());
+    check(rt_render_texture_views(bvh.handle(), c.data(), (int)c.size(), &p, W, H, all.data(), nullptr, nullptr,
+                                  nullptr),
+          "renderTextureViews");
     screens.assign(cameras.size(), {});
     for (size_t v = 0; v < cameras.size(); ++v) screens[v].assign(all.begin() + v * frame, all.begin() + (v + 1) * frame);
 }

@@ -2,6 +2,8 @@
 //   rt_scene_load_obj  <- loadMesh (src/mesh.cpp:58-188)
 //   rt_scene_preset    <- loadScene (src/scene.cpp:4-150)
 //   rt_camera_from_trackball <- Trackball::position / generateRay constants (framework/src/trackball.cpp:65-98)
+//   rt_camera_rays     <- Trackball::generateRay per pixel (framework/src/trackball.cpp:87-98, src/main.cpp:350-354)
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <exception>
@@ -215,5 +217,30 @@ extern "C" int rt_camera_from_trackball(const float look_at[3], const float e[3]
     out->quat[3] = w;
     out->half_height = std::tan(fovy / 2.0f);
     out->half_width = aspect * out->half_height;
+    return RT_OK;
+}
+
+// Trackball::generateRay (framework/src/trackball.cpp:87-98) for every pixel of a W x H frame, with the render
+// loop's pixel -> NDC rule (src/main.cpp:350-354): the kernels' gen_ray arithmetic (rt_math.h, the same
+// operation order on host and device), so rays_out[y * W + x] carries the bits the device traces for pixel
+// (x, y) -- reference y, before setPixel's flip.
+extern "C" int rt_camera_rays(const rt_camera* cam, int W, int H, rt_ray* rays_out) {
+    if (!cam || !rays_out || W <= 0 || H <= 0) {
+        set_error("rt_camera_rays: invalid argument");
+        return RT_ERR_INVALID;
+    }
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            const float ndx = (float)x / (float)W * 2.0f - 1.0f;
+            const float ndy = (float)y / (float)H * 2.0f - 1.0f;
+            const v3 csd = normalize(v3{-ndx * cam->half_width, ndy * cam->half_height, 1.0f});
+            const v3 d = quat_rotate(cam->quat[0], cam->quat[1], cam->quat[2], cam->quat[3], csd);
+            rt_ray& r = rays_out[(size_t)y * W + x];
+            for (int k = 0; k < 3; ++k) r.origin[k] = cam->position[k];
+            r.direction[0] = d.x;
+            r.direction[1] = d.y;
+            r.direction[2] = d.z;
+            r.t = FLT_MAX;  // a fresh Ray
+        }
     return RT_OK;
 }

@@ -30,6 +30,7 @@
 #include "rt_kernels.hip"
 #include "rt_megakernel.hip"
 #include "rt_wavefront.hip"
+#include "rt_texture_view.hip"
 
 using namespace rt;
 
@@ -1835,6 +1836,151 @@ extern "C" int rt_render_views(rt_ctx* c, const rt_camera* cams, int n_views, co
     rc = render_split(c, cams, n_views, p, W, H, 8, 0, 1, c->d_img, c->stream, &local);
     if (rc != RT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(rgb_out, c->d_img, view_img * n_views * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (stats) *stats = local;
+    return RT_OK;
+}
+
+// ---- the texture-debug view (rt_texture_view.hip): renderRayTracing(..., textureDebugging = true) ----
+// One replica's part: the bands b % band_count == band_rank of every view, one wave per 8x8 tile, each pixel's
+// colour (and first-hit primitive and depth, where asked for) at its setPixel place.  The kernel is no class of
+// the kernel plan: it is launched from here directly.
+static int launch_texture_view(rt_ctx* c, const rt_camera* cams, int n_views, const rt_params* p, int W, int H,
+                               int band_rows, int band_rank, int band_count, float* d_images, int32_t* d_prim,
+                               float* d_t, hipStream_t st, rt_stats* stats) {
+    HIP_TRY(hipSetDevice(c->device));
+    KParams K;
+    int rc = fill_params(c, cams, p, W, H, K);
+    if (rc != RT_OK) return rc;
+    // the view reads mat.kdTexture whatever useTextures says (src/main.cpp:95-105), and never samples a pixel twice
+    K.S.tex_on = c->S.ntex > 0 ? 1 : 0;
+    K.aa = K.multi = 0;
+    const int nbands = (H + band_rows - 1) / band_rows;
+    K.band_rows = band_rows;
+    K.band_rank = band_rank;
+    K.band_count = band_count;
+    K.n_local_bands = nbands > band_rank ? (nbands - band_rank + band_count - 1) / band_count : 0;
+    const long long tiles = (long long)((W + 7) / 8) * ((band_rows + 7) / 8) * K.n_local_bands;
+    if (tiles * 64 * n_views > 0x7FFFFFFFll || (long long)W * H * n_views * 3 >= (1ll << 40) ||
+        (tiles > 0 && texture_view_grid((int)tiles, n_views) > 0x7FFFFFFFll)) {
+        set_error("texture view: batch too large (job index overflows int)");
+        return RT_ERR_INVALID;
+    }
+    K.out = d_images;
+    K.out_image = 1;
+    K.view_rows = H;
+    K.n_views = n_views;
+    K.view_jobs = (int)(tiles * 64);
+    rc = upload_views(c, cams, n_views, st, K);  // the kernel reads every camera from the table (gen_ray_view)
+    if (rc != RT_OK) return rc;
+    c->wf_last_cnt = nullptr;
+    long long rows = 0;  // image rows of this rank's bands
+    for (int lb = 0; lb < K.n_local_bands; ++lb)
+        rows += std::min(band_rows, H - (lb * band_count + band_rank) * band_rows);
+    const bool deep = !c->df_ok;  // the BVH8 is deeper than the short stack
+    if (tiles > 0) {
+        const TexViewOut O{d_images, d_prim, d_t};
+        const unsigned grid = (unsigned)texture_view_grid((int)tiles, n_views);
+        HIP_TRY(hipEventRecord(c->ev0, st));
+        if (deep) hipLaunchKernelGGL(texture_view_kernel<RT_STACK_SIZE>, dim3(grid), dim3(64), 0, st, K, O);
+        else hipLaunchKernelGGL(texture_view_kernel<RT_STACK8>, dim3(grid), dim3(64), 0, st, K, O);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev1, st));
+    }
+    std::snprintf(c->last_kernel, sizeof(c->last_kernel), "rt::texture_view_kernel<%d>", deep ? RT_STACK_SIZE : RT_STACK8);
+    if (!stats) return RT_OK;
+    HIP_TRY(hipStreamSynchronize(st));
+    std::memset(stats, 0, sizeof(*stats));
+    stats->rays = (uint64_t)(rows * W * n_views);  // pixels rendered: one camera ray each
+    if (tiles > 0) HIP_TRY(hipEventElapsedTime(&stats->kernel_ms, c->ev0, c->ev1));
+    stats->node_bytes = RT_NODE_DW * 4u;
+    std::memcpy(stats->kernel, c->last_kernel, sizeof(stats->kernel));
+    return RT_OK;
+}
+
+// The view over a multi-device context: where every replica stores straight into devices[0]'s images
+// (rt_ctx_peer_stores all 1, and the images are not another process's) the bands split over the devices as in
+// render_split, for all three outputs; otherwise the whole call runs on devices[0] (no band-dense copy path
+// for this view).
+static int texture_view_split(rt_ctx* c, const rt_camera* cams, int n_views, const rt_params* p, int W, int H,
+                              int band_rows, int band_rank, int band_count, float* d_images, int32_t* d_prim,
+                              float* d_t, hipStream_t st, rt_stats* stats) {
+    const int n = std::max<int>(1, (int)c->replicas.size());
+    bool split = n > 1 && !ipc_mapped(d_images) && !(d_prim && ipc_mapped(d_prim)) && !(d_t && ipc_mapped(d_t));
+    for (int i = 1; i < n && split; ++i) split = c->replicas[i]->peer_ok && c->replicas[i]->opt_peer != 0;
+    if (!split)
+        return launch_texture_view(c, cams, n_views, p, W, H, band_rows, band_rank, band_count, d_images, d_prim, d_t,
+                                   st, stats);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventRecord(c->ev_ready, st));
+    std::vector<rt_stats> rs(n);
+    std::vector<int> rcs(n, RT_OK);
+    std::vector<std::string> errs(n);
+    const int count = band_count * n;
+    for (int i = 1; i < n; ++i) {
+        c->workers[i]->post([&, i] {
+            rt_ctx* r = c->replicas[i];
+            rcs[i] = hipSetDevice(r->device) == hipSuccess && hipStreamWaitEvent(r->stream, c->ev_ready, 0) == hipSuccess
+                         ? RT_OK : RT_ERR_HIP;
+            if (rcs[i] == RT_OK)
+                rcs[i] = launch_texture_view(r, cams, n_views, p, W, H, band_rows, band_rank + band_count * i, count,
+                                             d_images, d_prim, d_t, r->stream, stats ? &rs[i] : nullptr);
+            if (rcs[i] == RT_OK && hipEventRecord(r->ev_done, r->stream) != hipSuccess) rcs[i] = RT_ERR_HIP;
+            if (rcs[i] != RT_OK) errs[i] = last_error_text();
+        });
+    }
+    rcs[0] = launch_texture_view(c, cams, n_views, p, W, H, band_rows, band_rank, count, d_images, d_prim, d_t, st,
+                                 stats ? &rs[0] : nullptr);
+    if (rcs[0] != RT_OK) errs[0] = last_error_text();
+    for (int i = 1; i < n; ++i) c->workers[i]->wait();
+    HIP_TRY(hipSetDevice(c->device));
+    for (int i = 1; i < n; ++i)
+        if (rcs[i] == RT_OK) HIP_TRY(hipStreamWaitEvent(st, c->replicas[i]->ev_done, 0));
+    for (int i = 0; i < n; ++i)
+        if (rcs[i] != RT_OK) {
+            set_error(errs[i].empty() ? "texture view failed on device " + std::to_string(c->devices[i]) : errs[i]);
+            return rcs[i];
+        }
+    if (stats) {
+        *stats = rs[0];
+        for (int i = 1; i < n; ++i) add_stats(*stats, rs[i]);
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_render_texture_views_image_device(rt_ctx* c, const rt_camera* cams, int n_views, const rt_params* p,
+                                                    int W, int H, int band_rows, int band_rank, int band_count,
+                                                    float* d_images, int32_t* d_prim, float* d_t, void* stream,
+                                                    rt_stats* stats) {
+    if (!c || !cams || n_views <= 0 || !p || !d_images || W <= 0 || H <= 0 || band_rows <= 0 || band_count <= 0 ||
+        band_rank < 0 || band_rank >= band_count) {
+        set_error("rt_render_texture_views_image_device: invalid argument");
+        return RT_ERR_INVALID;
+    }
+    return texture_view_split(c, cams, n_views, p, W, H, band_rows, band_rank, band_count, d_images, d_prim, d_t,
+                              (hipStream_t)stream, stats);
+}
+
+// The view for a batch of cameras to host memory: rendered into the context's images on devices[0] (rgb, then
+// prim and t where asked for, in one allocation) and copied out.
+extern "C" int rt_render_texture_views(rt_ctx* c, const rt_camera* cams, int n_views, const rt_params* p, int W, int H,
+                                       float* rgb_out, int32_t* prim_out, float* t_out, rt_stats* stats) {
+    if (!c || !cams || n_views <= 0 || !p || !rgb_out || W <= 0 || H <= 0) {
+        set_error("rt_render_texture_views: invalid argument");
+        return RT_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t px = (size_t)W * H * n_views;
+    int rc = ensure(c, &c->d_img, &c->img_bytes, px * 5 * sizeof(float));
+    if (rc != RT_OK) return rc;
+    int32_t* d_prim = prim_out ? reinterpret_cast<int32_t*>(c->d_img + px * 3) : nullptr;
+    float* d_t = t_out ? c->d_img + px * 4 : nullptr;
+    rt_stats local{};
+    rc = texture_view_split(c, cams, n_views, p, W, H, 8, 0, 1, c->d_img, d_prim, d_t, c->stream, &local);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(rgb_out, c->d_img, px * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (d_prim) HIP_TRY(hipMemcpyAsync(prim_out, d_prim, px * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (d_t) HIP_TRY(hipMemcpyAsync(t_out, d_t, px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (stats) *stats = local;
     return RT_OK;

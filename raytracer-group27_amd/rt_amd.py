@@ -138,6 +138,7 @@ EXPORTS = [
     "rt_update_lights", "rt_update_materials", "rt_unpermute_views_device", "rt_scene_mesh_count", "rt_scene_mesh_get",
     "rt_ctx_devices", "rt_ctx_peer_stores", "rt_render_views_image_device", "rt_ipc_alloc", "rt_ipc_open", "rt_ipc_close", "rt_device_free",
     "rt_device_synchronize", "rt_memcpy_dtoh", "rt_debug_slab_check", "rt_source_hash",
+    "rt_render_texture_views_image_device", "rt_render_texture_views", "rt_camera_rays",
 ]
 IPC_HANDLE_BYTES = 64
 
@@ -295,6 +296,12 @@ def lib():
             "rt_ctx_peer_stores": ([vp, P(C.c_int), C.c_int], C.c_int),
             "rt_render_views_image_device": ([vp, P(rt_camera), C.c_int, P(rt_params), C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, vp, vp, P(rt_stats)], C.c_int),
+            "rt_render_texture_views_image_device": ([vp, P(rt_camera), C.c_int, P(rt_params), C.c_int, C.c_int,
+                                                      C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, P(rt_stats)],
+                                                     C.c_int),
+            "rt_render_texture_views": ([vp, P(rt_camera), C.c_int, P(rt_params), C.c_int, C.c_int, P(C.c_float),
+                                         P(C.c_int32), P(C.c_float), P(rt_stats)], C.c_int),
+            "rt_camera_rays": ([P(rt_camera), C.c_int, C.c_int, vp], C.c_int),
             "rt_ipc_alloc": ([C.c_int, C.c_size_t, P(vp), P(C.c_uint8)], C.c_int),
             "rt_ipc_open": ([C.c_int, P(C.c_uint8), P(vp)], C.c_int),
             "rt_ipc_close": ([vp], C.c_int),
@@ -466,6 +473,14 @@ def camera_from_trackball(look_at=(0.0, 0.0, 0.0), euler=None, distance=3.0, fov
     check(lib().rt_camera_from_trackball(la, eu, float(np.float32(distance)), float(np.float32(fovy)),
                                          float(np.float32(aspect)), C.byref(cam)), "camera")
     return cam
+
+
+def camera_rays(cam, W, H):
+    """rt_camera_rays: Trackball::generateRay for every pixel of a W x H frame (host only), a RAY_DTYPE array
+    with pixel (x, y) at y * W + x -- reference y, before setPixel's flip -- and t = FLT_MAX."""
+    rays = np.zeros(max(0, W) * max(0, H), RAY_DTYPE)
+    check(lib().rt_camera_rays(C.byref(cam), W, H, rays.ctypes.data), "rt_camera_rays")
+    return rays
 
 
 RADIANS = np.float32(0.01745329251994329576923690768489)
@@ -660,6 +675,41 @@ class Context:
         check(lib().rt_render_views_image_device(self.h, arr, len(cams), C.byref(prm), W, H, band_rows, band_rank,
                                                  band_count, C.c_void_p(d_images_ptr), C.c_void_p(stream_ptr or 0),
                                                  C.byref(st) if stats else None), "rt_render_views_image_device")
+        return st
+
+    def render_texture_views(self, cams, prm, W, H, hits=False):
+        """The texture-debug view (renderRayTracing(..., textureDebugging=True)) of a batch of cameras to host
+        memory (rt_render_texture_views): (rgb float32 [n_views, W*H*3], stats), or with hits=True
+        (rgb, prim int32 [n_views, W*H], t float32 [n_views, W*H], stats) -- the first hit's primitive (-1: none)
+        and depth (FLT_MAX: none) per pixel, all in Screen::m_textureData order."""
+        arr = (rt_camera * len(cams))(*cams)
+        rgb = np.zeros((len(cams), W * H * 3), np.float32)
+        prim = np.zeros((len(cams), W * H), np.int32) if hits else None
+        t = np.zeros((len(cams), W * H), np.float32) if hits else None
+        st = rt_stats()
+        check(lib().rt_render_texture_views(self.h, arr, len(cams), C.byref(prm), W, H,
+                                            rgb.ctypes.data_as(C.POINTER(C.c_float)),
+                                            prim.ctypes.data_as(C.POINTER(C.c_int32)) if hits else None,
+                                            t.ctypes.data_as(C.POINTER(C.c_float)) if hits else None, C.byref(st)),
+              "rt_render_texture_views")
+        return (rgb, prim, t, st) if hits else (rgb, st)
+
+    def render_texture_view(self, cam, prm, W, H, hits=False):
+        """render_texture_views for one camera: (rgb [W*H*3], stats) or (rgb, prim [W*H], t [W*H], stats)."""
+        out = self.render_texture_views([cam], prm, W, H, hits)
+        return tuple(a[0] for a in out[:-1]) + (out[-1],)
+
+    def render_texture_views_image_device(self, cams, prm, W, H, d_images_ptr, d_prim_ptr=None, d_t_ptr=None,
+                                          stream_ptr=None, band_rows=8, band_rank=0, band_count=1, stats=True):
+        """rt_render_texture_views_image_device: the view's pixels straight into d_images (setPixel layout, view v
+        at v*W*H*3) and, where given, the first hits' primitives / depths into d_prim / d_t (view v at v*W*H);
+        this call renders bands b % band_count == band_rank.  stats=False keeps the call asynchronous."""
+        arr = (rt_camera * len(cams))(*cams)
+        st = rt_stats() if stats else None
+        check(lib().rt_render_texture_views_image_device(
+            self.h, arr, len(cams), C.byref(prm), W, H, band_rows, band_rank, band_count, C.c_void_p(d_images_ptr),
+            C.c_void_p(d_prim_ptr or 0), C.c_void_p(d_t_ptr or 0), C.c_void_p(stream_ptr or 0),
+            C.byref(st) if stats else None), "rt_render_texture_views_image_device")
         return st
 
     def intersect(self, rays, use_bvh):

@@ -21,6 +21,7 @@ STUB(rt_debug_job_trace) STUB(rt_debug_records) STUB(rt_debug_wave_trace) STUB(r
 STUB(rt_device_free) STUB(rt_device_synchronize) STUB(rt_intersect) STUB(rt_ipc_alloc) STUB(rt_ipc_close)
 STUB(rt_ipc_open) STUB(rt_memcpy_dtoh) STUB(rt_philox4x32_10) STUB(rt_postprocess) STUB(rt_postprocess_device)
 STUB(rt_render) STUB(rt_render_device) STUB(rt_render_views) STUB(rt_render_views_device)
-STUB(rt_render_views_image_device) STUB(rt_selftest_math) STUB(rt_set_build_mode) STUB(rt_set_counting)
+STUB(rt_render_views_image_device) STUB(rt_render_texture_views)
+STUB(rt_render_texture_views_image_device) STUB(rt_selftest_math) STUB(rt_set_build_mode) STUB(rt_set_counting)
 STUB(rt_shade) STUB(rt_texture_sample) STUB(rt_unpermute_bands_device) STUB(rt_unpermute_views_device)
 STUB(rt_update_lights) STUB(rt_update_materials)
